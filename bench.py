@@ -12,7 +12,9 @@ neighbours' rows, or exchanged before it: the transport probe picks at setup).
 tol is disabled so every timed step does real work; the device-side iteration
 counter is checked after the run.
 
-  python bench.py                      # N=1
+  python bench.py                      # N=1: set up, warm up, time the steps, print the result line
+  python bench.py --full               # ... then the true-residual check and the per-phase timing (check.*)
+  python bench.py --dump-outputs DIR   # ... and x, rnorm of the last timed step as DIR/*.npy
   python bench.py --gpus 8             # starts 8 ranks itself (one process per GPU, RCCL)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
       --master-addr 127.0.0.1 --master-port 29500 bench.py --gpus 8   # same ranks under torchrun
@@ -33,6 +35,8 @@ import time
 
 METRIC = "CG iterations/sec (whole node), 5-pt Poisson N=16384², 1/2/4/8 MI355X"
 BASELINE_IT_PER_S = 65.0  # BASELINE.md "Bar to clear": reference algorithm's H100 roofline (derived; nothing published)
+DUMP_BYTES = 32 << 20  # --dump-outputs: all ranks' x files together stay within this
+DUMP_SEED = 20240607  # ... and a longer x is sampled at these seeded rows (the same rows in every run)
 
 
 def aggregate(steps, ranks):
@@ -91,6 +95,29 @@ def probe_report(info, probed_ar):
     return r
 
 
+def sample_rows(n, limit, seed=DUMP_SEED):
+    """The rows of an n-vector that --dump-outputs keeps: all of them (None) when n <= limit, else limit
+    sorted rows drawn with a fixed seed -- a function of (n, limit, seed) only, so two builds keep the same rows."""
+    import numpy as np
+
+    if n <= limit:
+        return None
+    return np.sort(np.random.default_rng(seed).integers(0, n, size=limit))
+
+
+def dump_outputs(directory, x, rnorm, rank, world):
+    """Write the timed path's results: this rank's x (float64, sampled by sample_rows to its share of
+    DUMP_BYTES) and, from rank 0, the recurrence residual norm."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    x = np.asarray(x, dtype=np.float64)
+    rows = sample_rows(x.size, DUMP_BYTES // 8 // max(world, 1), DUMP_SEED + rank)
+    np.save(os.path.join(directory, "x.npy" if rank == 0 else f"x_rank{rank}.npy"), x if rows is None else x[rows])
+    if rank == 0:
+        np.save(os.path.join(directory, "rnorm.npy"), np.array([rnorm], dtype=np.float64))
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None)
@@ -118,12 +145,22 @@ def parse_args(argv=None):
     ap.add_argument("--graph", action="store_true", help="(default since r2; kept for old command lines)")
     ap.add_argument("--no-overlap", action="store_true")
     ap.add_argument("--blocks-per-cu", type=int, default=0, help="SpMV grid; 0 = auto")
-    ap.add_argument("--no-verify", action="store_true", help="skip the true-residual check ||b-Ax|| after the run")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run what the headline figure does not need: the true-residual "
+                         "check ||b-Ax|| (check.true_*) and the per-phase timing (--phases, check.phase_us).  A plain "
+                         "run sets up, warms up, times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what they computed as DIR/<name>.npy (float64): x (this rank's "
+                         "rows of the solution after the last timed step; a seeded sample of %d MB when larger) and "
+                         "rnorm (the recurrence residual norm).  Ranks other than 0 write x_rank<r>.npy"
+                         % (DUMP_BYTES >> 20))
+    ap.add_argument("--no-verify", action="store_true", help="--full: skip the true-residual check ||b-Ax|| after the run")
     ap.add_argument("--set", action="append", default=[], metavar="KEY=VALUE",
                     help="experiment: set a native CgOptions field (e.g. halo_pull=0, placement_tries=1)")
     ap.add_argument("--phases", type=int, default=10,
-                    help="after the timed region: N more iterations with per-phase hipEvent timing (diagnostic, "
-                         "reported under check.phase_us of rank 0 and check.phase_us_max over ranks; 0 = off)")
+                    help="--full, after the timed region: N more iterations with per-phase hipEvent timing (diagnostic, "
+                         "reported under check.phase_us of rank 0 and check.phase_us_max over ranks; 0 = off, and off "
+                         "with --dump-outputs, which ends the solve at the last timed step)")
     ap.add_argument("--comm", default="single", choices=["dual", "single"],
                     help="single (default): one RCCL communicator, every collective in one stream order on the "
                          "compute stream; dual: reduce + halo communicators, the halo on the side stream next to the "
@@ -280,9 +317,15 @@ def _run_rank(args, out_fd) -> int:
     barrier()
     dt = time.perf_counter() - t0
 
+    if args.dump_outputs:
+        # what the timed steps computed: finalize completes x_m (the single-reduction form pairs x updates)
+        # and ends the solve there, so the phase iterations, which would carry x on, do not run after it
+        solver.finalize()
+        dump_outputs(args.dump_outputs, solver.x_local(), solver.result()["rnorm"], env.rank, env.world)
 
     phases = None
-    if args.phases > 0 and solver.info["recurrence"] == "single-reduction":
+    if (args.full and args.phases > 0 and not args.dump_outputs
+            and solver.info["recurrence"] == "single-reduction"):
         phases = solver.phase_profile(args.phases)  # untimed diagnostics: per-phase mean microseconds
         phases = {k: round(v, 2) for k, v in phases.items()}
     n_extra = args.phases if phases is not None else 0
@@ -290,7 +333,7 @@ def _run_rank(args, out_fd) -> int:
     res = solver.result()
     ok = res["iterations"] == args.warmup + args.steps + n_extra and not res["breakdown"] and math.isfinite(res["rnorm"])
     extra = {}
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         # the recurrence residual must track the true residual ||b - A x|| (catches a kernel
         # that does less work than claimed: its residual would drift from the truth by orders
         # of magnitude).  Over the bench's few hundred iterations the two agree to ~1e-15

@@ -31,7 +31,9 @@ C5SCR = "--problem randspd --rows 100000000 --band 410 --density 1.0 --scramble 
 
 
 def bench(extra: str = "") -> str:
-    return f"{PY} bench.py {extra}".strip()
+    """The bench with its checks (--full: true residual, per-phase timing); the A/B recipes below that
+    compare headline figures only spell out a plain run."""
+    return f"{PY} bench.py --full {extra}".strip()
 
 
 def prof(tag: str, cmd: str, pmc: str = "", fmt: str = "csv") -> str:

@@ -47,7 +47,7 @@ def test_bench_sdma_halo_rehearsal_on_one_gpu():
     the solver's halo goes through PeerHaloComm inside the 32-iteration graphs (flags replayed),
     collectives of the all-reduce move nothing (rehearsal); every rank ok and latched together."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr",
-           "127.0.0.1", "--master-port", str(_port()), "bench.py", "--gpus", "2", "--rehearse-ranks", "--grid",
+           "127.0.0.1", "--master-port", str(_port()), "bench.py", "--full", "--gpus", "2", "--rehearse-ranks", "--grid",
            "2048", "--steps", "64", "--warmup", "8", "--phases", "0", "--watchdog", "60", "--halo-transport", "sdma"]
     p = _run(cmd)
     assert p.returncode == 0, p.stdout + p.stderr
@@ -118,7 +118,7 @@ def test_bench_ipc_allreduce_rehearsal_is_a_real_solve():
     """bench.py --rehearse-ranks --allreduce ipc: the P-rank bench on one GPU with the IPC all-reduce is a
     real solve, so its check requires the recurrence residual to track ||b - A x||."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr",
-           "127.0.0.1", "--master-port", str(_port()), "bench.py", "--gpus", "2", "--rehearse-ranks", "--grid",
+           "127.0.0.1", "--master-port", str(_port()), "bench.py", "--full", "--gpus", "2", "--rehearse-ranks", "--grid",
            "2048", "--steps", "64", "--warmup", "8", "--phases", "0", "--watchdog", "60", "--allreduce", "ipc"]
     p = _run(cmd)
     assert p.returncode == 0, p.stdout + p.stderr

@@ -107,8 +107,8 @@ def test_bench_launcher_processes(world, problem, comm):
     extra = (["--grid", "512"] if problem == "poisson2d"
              else ["--problem", "randspd", "--rows", "200000", "--band", "64", "--density", "0.5"]
              + (["--scramble", "1"] if problem == "randspd_scrambled" else []))
-    p = _run([sys.executable, "bench.py", "--gpus", str(world), "--steps", "40", "--warmup", "5", "--comm", comm]
-             + extra)
+    p = _run([sys.executable, "bench.py", "--full", "--gpus", str(world), "--steps", "40", "--warmup", "5", "--comm",
+              comm] + extra)
     assert p.returncode == 0, p.stdout + p.stderr
     line = json.loads(p.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == world and line["check"]["comm_world"] == world
@@ -122,8 +122,8 @@ def test_bench_matches_single_gpu_fixed_iterations(world):
     """Same fixed iterations at P = 1 and P: the recurrence residual agrees to rounding."""
     out = []
     for p_ in (1, world):
-        p = _run([sys.executable, "bench.py", "--gpus", str(p_), "--grid", "1024", "--steps", "100", "--warmup", "0",
-                  "--phases", "0"])
+        p = _run([sys.executable, "bench.py", "--full", "--gpus", str(p_), "--grid", "1024", "--steps", "100",
+                  "--warmup", "0", "--phases", "0"])
         assert p.returncode == 0, p.stdout + p.stderr
         out.append(json.loads(p.stdout.strip().splitlines()[-1]))
     r1, rp = out[0]["check"]["rnorm"], out[1]["check"]["rnorm"]
@@ -145,7 +145,7 @@ def test_bench_default_transport_probed_and_matches_one_gpu(world):
     for tag, extra in (("one", ["--gpus", "1"]), ("auto", ["--gpus", str(world)]),
                        ("noprobe", ["--gpus", str(world), "--set", "transport_probe=0"]),
                        ("rccl", ["--gpus", str(world), "--halo-transport", "rccl", "--allreduce", "rccl"])):
-        p = _run([sys.executable, "bench.py"] + extra + args)
+        p = _run([sys.executable, "bench.py", "--full"] + extra + args)
         assert p.returncode == 0, (tag, p.stdout + p.stderr)
         out[tag] = json.loads(p.stdout.strip().splitlines()[-1])
         assert out[tag]["check"]["ok"] and out[tag]["check"]["graph_fallbacks"] == 0, (tag, out[tag]["check"])
@@ -235,8 +235,8 @@ def test_bench_multiprocess_rehearsal_on_one_gpu(route, world):
     """The P-rank bench's host side on ONE GPU, every round: P processes (bench.py's own launcher,
     or torchrun) on device 0 with collectives that move nothing, but the real gloo rendezvous,
     barriers, all_gather_object aggregation and slowest-rank JSON line of the scaling runs."""
-    args = ["bench.py", "--gpus", str(world), "--rehearse-ranks", "--grid", "1024", "--steps", "10", "--warmup", "2",
-            "--phases", "0", "--watchdog", "60"]
+    args = ["bench.py", "--full", "--gpus", str(world), "--rehearse-ranks", "--grid", "1024", "--steps", "10",
+            "--warmup", "2", "--phases", "0", "--watchdog", "60"]
     if route == "spawn":
         cmd = [sys.executable] + args
     else:

@@ -130,6 +130,43 @@ def test_bench_pass_labels():
     assert "lean" not in bench.pass_label(dict(carry3, lean_only=False), "poisson3d")
 
 
+def test_bench_plain_run_options():
+    """A plain run does neither the true-residual check nor the phase timing (--full turns both on), and
+    writes nothing unless --dump-outputs names a directory."""
+    bench = _bench_module()
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert not a.full and a.dump_outputs is None and a.steps == 7 and a.warmup == 3
+    a = bench.parse_args(["--full", "--dump-outputs", "d"])
+    assert a.full and a.dump_outputs == "d" and a.phases == 10 and not a.no_verify
+
+
+def test_bench_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs writes float64 arrays: the whole x when it fits, else a sample of rows that depends
+    on the length, the limit and the seed only (two runs, or two builds, keep the same rows), every
+    rank's share of the limit; rnorm from rank 0."""
+    import numpy as np
+
+    bench = _bench_module()
+    x = np.arange(1000, dtype=np.float64) * 0.5
+    bench.dump_outputs(str(tmp_path / "a"), x, 3.25, 0, 1)
+    got = np.load(tmp_path / "a" / "x.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, x)
+    assert np.load(tmp_path / "a" / "rnorm.npy").tolist() == [3.25]
+    monkeypatch.setattr(bench, "DUMP_BYTES", 8 * 200)  # 200 values over all ranks
+    for d in ("b", "c"):
+        for rank in (0, 1):
+            bench.dump_outputs(str(tmp_path / d), x, 3.25, rank, 2)
+    b0, b1 = np.load(tmp_path / "b" / "x.npy"), np.load(tmp_path / "b" / "x_rank1.npy")
+    assert b0.dtype == np.float64 and b0.size == 100 and b1.size == 100
+    assert sorted(os.listdir(tmp_path / "b")) == ["rnorm.npy", "x.npy", "x_rank1.npy"]
+    assert np.array_equal(b0, np.load(tmp_path / "c" / "x.npy"))
+    assert np.array_equal(b1, np.load(tmp_path / "c" / "x_rank1.npy"))
+    rows = bench.sample_rows(1000, 100, bench.DUMP_SEED)
+    assert np.array_equal(b0, x[rows]) and np.all(np.diff(rows) >= 0) and rows.min() >= 0 and rows.max() < 1000
+    assert len(set(rows.tolist())) > 80 and not np.array_equal(b0, b1)  # spread over x; ranks draw their own rows
+    assert bench.sample_rows(100, 100) is None
+
+
 def test_kfd_gpu_count_from_a_fake_topology(tmp_path):
     """The launcher counts GPUs without HIP: KFD topology nodes with a nonzero gfx_target_version
     whose render node this process can open (a container sees the host's topology, not its cards)."""
