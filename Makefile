@@ -45,6 +45,9 @@ $(BUILD)/%.o: csrc/%.hip $(HEADERS)
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
+# preconditioned CG: the compiler's per-kernel resource usage (VGPRs, scratch: must stay 0) in the build log
+$(BUILD)/gpu/cg_pcg.o: HIPFLAGS += -Rpass-analysis=kernel-resource-usage
+
 $(BUILD)/%.o: csrc/%.cpp $(HEADERS)
 	@mkdir -p $(dir $@)
 	$(CXX) $(CXXFLAGS) -c $< -o $@

@@ -23,6 +23,8 @@
 //   --checkpoint PREFIX  --checkpoint-every K  --resume PREFIX  --inject-nan-at K
 //   --print-x auto|yes|no  --report text|json  --verify
 //   --halo-transport auto|rccl  --allreduce auto|rccl|ipc  --transport-probe auto|off  --rehearse-ranks
+//   --precond none|jacobi|chebyshev  --cheb-degree M  --cheb-ratio R  --cheb-lmax L (beyond the reference:
+//   preconditioned CG, csrc/gpu/cg_pcg.hip; not with an explicit --recurrence, --sim-ranks > 1 or checkpoints)
 // Multi-GPU runs use one host thread per GPU inside this process (no MPI in
 // this image); the two RCCL unique ids are shared in memory.  At P > 1 each rank's
 // communicator is wrapped in a PeerHaloComm that maps the other threads' halo
@@ -175,6 +177,16 @@ Args parse(int argc, char** argv) {
       a.recurrence_set = true;
     }
     else if (f == "--pipe-rr") a.opt.pipe_rr = std::stoi(need(i));
+    else if (f == "--precond") {
+      const std::string v = need(i);
+      if (v == "none") a.opt.precond = 0;
+      else if (v == "jacobi") a.opt.precond = 1;
+      else if (v == "chebyshev") a.opt.precond = 2;
+      else usage_error("--precond " + v);
+    }
+    else if (f == "--cheb-degree") a.opt.cheb_degree = std::stoi(need(i));
+    else if (f == "--cheb-ratio") a.opt.cheb_ratio = std::stod(need(i));
+    else if (f == "--cheb-lmax") a.opt.cheb_lmax = std::stod(need(i));
     else if (f == "--window") a.opt.form.window = tri(need(i), "--window");
     else if (f == "--carry") a.opt.form.carry = tri(need(i), "--carry");
     else if (f == "--interleave") a.opt.form.interleave = tri(need(i), "--interleave");
@@ -207,6 +219,13 @@ Args parse(int argc, char** argv) {
   // single-reduction form); the built-in demo keeps the reference's CSR and two-reduction order
   if (a.spec.kind != ProblemKind::Demo && !a.format_set) a.opt.format = 3;
   if (a.spec.kind != ProblemKind::Demo && !a.recurrence_set) a.opt.recurrence = -1;
+  if (a.opt.precond != 0) {
+    if (a.recurrence_set && a.opt.recurrence != -1) usage_error("--precond selects its own recurrence (not with --recurrence)");
+    if (a.cpu && a.sim_ranks > 1) usage_error("--precond on the cpu runs one rank (not with --sim-ranks)");
+    if (!a.opt.checkpoint_path.empty() || a.opt.checkpoint_every > 0 || !a.resume.empty())
+      usage_error("checkpoints are not supported with --precond");
+    a.opt.recurrence = -1;
+  }
   // default grids, as make_problem(): 1024^2 (BASELINE config 1's size) and 128^3
   if (a.spec.kind == ProblemKind::Poisson2D && a.spec.N == 3) a.spec.N = 1024;
   if (a.spec.kind == ProblemKind::Poisson3D && a.spec.N == 3) a.spec.N = 128;
@@ -474,6 +493,7 @@ int main(int argc, char** argv) {
                 world < 2 || a.cpu ? "none" : info.halo_pull ? "in-kernel" : (a.rehearse ? "local" : "rccl"),
                 world < 2 || a.cpu ? "none" : info.alt_allreduce ? "ipc" : (a.rehearse ? "local" : "rccl"), probe,
                 a.rehearse ? "true" : "false");
+    if (a.opt.precond != 0) std::printf("\"precond\": \"%s\", ", a.opt.precond == 2 ? "chebyshev" : "jacobi");
     std::printf("\"problem\": \"%s\", \"n\": %lld, \"nnz_rank0\": %lld, \"ranks\": %d, \"device\": \"%s\", "
                 "\"format\": \"%s\", \"iterations\": %d, \"converged\": %s, \"breakdown\": %s, \"rnorm\": %.6e, "
                 "\"true_rnorm\": %.6e, \"setup_s\": %.6f, \"solve_s\": %.6f, \"it_per_s\": %.3f, "

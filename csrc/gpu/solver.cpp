@@ -31,6 +31,19 @@ GpuCgSolver::GpuCgSolver(const ProblemSpec& spec, const CgOptions& opt, int rank
     c8_ = opt_.format == 3;  // dictionary codes: decided in setup() from the actual entries (fallback d16)
     opt_.format = 1;
   }
+  check_precond_options(opt_);
+  if (opt_.precond != 0) {
+    // preconditioned CG (cg_pcg.hip) gathers z and p through the generic engines: plain CSR / SELL-64
+    // (int32, d16, c8) storage only.  The carries, tiles, SELL-64/aligned, dia4 / diav are all chosen for
+    // the single-reduction recurrence, so none is selected here; forcing one is an error
+    const PassForm& f = opt_.form;
+    MCG_CHECK(f.interleave != 1 && f.pipeline != 1 && f.carry != 1 && f.window != 1 && f.pmat != 1 && f.tiles != 1 &&
+                  f.sell_aligned != 1 && f.ap_recompute != 1 && f.carry_dia != 1 && f.carry_vc != 1 && f.p3 != 1 &&
+                  f.p3buf != 1 && f.halo_pull != 1 && f.lean_split != 1,
+              "a preconditioner runs on plain CSR / SELL-64 storage: the carry, tile, aligned and split pass forms "
+              "cannot be forced with it");
+    opt_.recurrence = 3;
+  }
   // auto: the single-reduction form (one pass, one all-reduce per iteration) when P > 1 or on
   // SELL, where its interleaved {r, Ap} gathers make it the faster pass (profiles/sweep_ra_*)
   if (opt_.recurrence < 0) opt_.recurrence = (world_ > 1 || opt_.format == 1) ? 1 : 0;
@@ -46,7 +59,8 @@ GpuCgSolver::GpuCgSolver(const ProblemSpec& spec, const CgOptions& opt, int rank
   if (use_comm_ && !comm_->graph_capturable()) opt_.use_graph = false;
   MCG_CHECK(opt_.graph_iters >= 2 && opt_.graph_iters % 2 == 0, "graph_iters must be even and >= 2");
   if (opt_.hooks.inject_nan_at >= 0) opt_.use_graph = false;  // the hook runs between eager iterations
-  MCG_CHECK(opt_.recurrence >= -1 && opt_.recurrence <= 2, "recurrence must be -1 (auto), 0, 1 or 2 (pipelined)");
+  MCG_CHECK(opt_.recurrence >= -1 && opt_.recurrence <= (opt_.precond != 0 ? 3 : 2),
+            "recurrence must be -1 (auto), 0, 1 or 2 (pipelined)");
   // pipelined CG: a residual replacement every pipe_rr iterations is an eager step (no capture)
   if (opt_.recurrence == 2 && opt_.pipe_rr != 0) opt_.use_graph = false;
   // halo prefetch crosses iteration (and graph-launch) boundaries: eager runs only (and not for
@@ -112,7 +126,8 @@ void GpuCgSolver::reset_state_() {
   const int64_t n = L_.n_local();
   hipStream_t s = s0_;
   MCG_HIP(hipMemsetAsync(x_.get(), 0, x_.bytes(), s), "device memset failed(x)");
-  for (DeviceBuffer<double>* v : {&Ap_, &r_, &ra_[0], &ra_[1], &ape_[0], &ape_[1], &apx_[0], &apx_[1], &w_, &z_, &q_})
+  for (DeviceBuffer<double>* v : {&Ap_, &r_, &ra_[0], &ra_[1], &ape_[0], &ape_[1], &apx_[0], &apx_[1], &w_, &z_, &q_,
+                                  &zc_[0], &zc_[1], &dch_})
     if (v->bytes()) MCG_HIP(hipMemsetAsync(v->get(), 0, v->bytes(), s), "device memset failed(r)");
   MCG_HIP(hipMemsetAsync(p_[0].get(), 0, p_[0].bytes(), s), "device memset failed(p)");
   MCG_HIP(hipMemsetAsync(p_[1].get(), 0, p_[1].bytes(), s), "device memset failed(p)");
@@ -133,8 +148,9 @@ void GpuCgSolver::reset_state_() {
       comm_->allreduce_sum(st_.get()->red, 4, s);
       comm_->allreduce_sum(&st_.get()->rr_new, 1, s);  // rr0 stays this rank's b.b (rr0_local)
     }
-  } else if (pmat_) {
+  } else if (pmat_ || opt_.recurrence == 3) {
     // U_0 forms r_0 = b - 0 * Ap and p_0 = r_0 + 0 * p: r = b, Ap = 0, p = 0
+    // (preconditioned: r holds owned rows only; z_0 = M r_0 and the first sums follow below)
     MCG_HIP(hipMemcpyAsync(r_.get(), b_.get(), n * sizeof(double), hipMemcpyDeviceToDevice, s),
             "vector copy failed(r)");
   } else if (opt_.form.interleave == 1) {
@@ -154,6 +170,10 @@ void GpuCgSolver::reset_state_() {
     kern::dot_partials(b_.get(), b_.get(), n, partials_.get(), g_b_, s);
     kern::cg_reduce(partials_.get(), g_b_, st_.get(), kReduceInit, 1, opt_.tol, s);
     if (use_comm_) comm_->allreduce_sum(&st_.get()->rr_new, 1, s);
+  }
+  if (opt_.recurrence == 3) {  // z_0 = M r_0, {r_0.r_0, r_0.z_0} -> red (p_0 = z_0 is formed by the first pass)
+    enqueue_precond_(0, 1);
+    if (use_comm_) comm_->allreduce_sum(st_.get()->red, 4, s);
   }
   MCG_HIP(hipStreamSynchronize(s), "compute norm2 failed(r)");
   if (opt_.rtol > 0) {  // relative stopping: tol = rtol * ||b|| (kernels take tol by value: re-capture)
@@ -596,8 +616,99 @@ void GpuCgSolver::enqueue_iteration_pipe_(int k) {
   }
 }
 
+// Preconditioned CG (cg_pcg.hip).  Everything on the compute stream: halo of {z_k, p_{k-1}}, the pass,
+// all-reduce of p.q, the update (and the Chebyshev steps, each behind a halo of z), all-reduce of {r.r, r.z}.
+kern::PcgVectors GpuCgSolver::pcg_vectors_(int k) {
+  kern::PcgVectors v{};
+  v.x = x_.get();
+  v.r = r_.get();
+  v.q = Ap_.get();
+  v.d = dch_.get();
+  v.dinv = dinv_.get();
+  v.z[0] = zc_[0].get();
+  v.z[1] = zc_[1].get();
+  v.p_old = p_[(k + 1) & 1].get();
+  v.p_new = p_[k & 1].get();
+  return v;
+}
+
+void GpuCgSolver::enqueue_precond_(int k, int init) {
+  const int64_t n = L_.n_local();
+  CgState* st = st_.get();
+  const kern::PcgVectors v = pcg_vectors_(k);
+  kern::RedCtl rc;
+  rc.cnt = red_cnt_.get();
+  rc.lvl2 = red_l2_.get();
+  rc.l2s = red_l2s_;
+  rc.top = red_l2s_;
+  rc.base = 0;
+  const int m = opt_.precond == 2 ? cheb_.m : 1;
+  const int mode = opt_.precond == 1 ? 0 : (m == 1 ? 1 : 2);
+  // (a transport whose readers pull later: every kernel below rewrites rows exchanged earlier)
+  if (use_halo_) comm_->halo_fence(s0_);
+  rc.ngroups = red_groups_b_;
+  kern::cg_pcg_update(mode, v, L_.own_off, n, cheb_.inv_theta, init, partials_.get(), pstride_, g_b_, st, s0_, rc);
+  rc.ngroups = red_groups_all_;
+  const int fmt = pcg_fmt_();
+  const SellDev S = sell_view();
+  for (int j = 1; j < m; ++j) {
+    const int zin = (j - 1) & 1, last = j == m - 1 ? 1 : 0;
+    if (use_halo_) {
+      double* zv[1] = {zc_[zin].get()};
+      comm_->halo_exchange(L_, zv, 1, s0_);
+      comm_->halo_fence(s0_);
+    }
+    if (info_.idx64)
+      kern::cg_pcg_cheb_step<int64_t>(fmt, info_.spmv_param, CsrDev<int64_t>{rp64_.get(), cols_.get(), vals_.get(), n},
+                                      S, v, zin, cheb_.c1[j], cheb_.c2[j], last, init, L_.own_off, tr_all_,
+                                      partials_.get(), pstride_, g_all_, st, s0_, rc);
+    else
+      kern::cg_pcg_cheb_step<int32_t>(fmt, info_.spmv_param, CsrDev<int32_t>{rp32_.get(), cols_.get(), vals_.get(), n},
+                                      S, v, zin, cheb_.c1[j], cheb_.c2[j], last, init, L_.own_off, tr_all_,
+                                      partials_.get(), pstride_, g_all_, st, s0_, rc);
+  }
+}
+
+void GpuCgSolver::enqueue_iteration_pcg_(int k) {
+  trace::Range tr_("mcg.iteration.preconditioned");
+  const int64_t n = L_.n_local();
+  CgState* st = st_.get();
+  const kern::PcgVectors v = pcg_vectors_(k);
+  const int m = opt_.precond == 2 ? cheb_.m : 1;
+  const int zsel = (m - 1) & 1;  // the buffer the last Chebyshev step (or the update) left z_k in
+  if (use_halo_) {
+    double* vecs[2] = {zc_[zsel].get(), p_[(k + 1) & 1].get()};
+    comm_->halo_exchange(L_, vecs, 2, s0_);
+    comm_->halo_fence(s0_);  // the pass rewrites p_k's buffer, exchanged as p_{k-2}'s an iteration ago
+  }
+  kern::RedCtl rc;
+  rc.cnt = red_cnt_.get();
+  rc.lvl2 = red_l2_.get();
+  rc.l2s = red_l2s_;
+  rc.top = red_l2s_;
+  rc.base = 0;
+  rc.ngroups = red_groups_all_;
+  rc.check = k >= 1 ? 1 : 0;  // the reference never tests r_0
+  rc.first = k == 0 ? 1 : 0;
+  const int fmt = pcg_fmt_();
+  const SellDev S = sell_view();
+  if (info_.idx64)
+    kern::cg_pcg_pass<int64_t>(fmt, info_.spmv_param, CsrDev<int64_t>{rp64_.get(), cols_.get(), vals_.get(), n}, S, v, zsel,
+                               L_.own_off, tr_all_, partials_.get(), pstride_, g_all_, st, opt_.tol, s0_, rc);
+  else
+    kern::cg_pcg_pass<int32_t>(fmt, info_.spmv_param, CsrDev<int32_t>{rp32_.get(), cols_.get(), vals_.get(), n}, S, v, zsel,
+                               L_.own_off, tr_all_, partials_.get(), pstride_, g_all_, st, opt_.tol, s0_, rc);
+  if (use_comm_) comm_->allreduce_sum(st->red, 4, s0_);
+  enqueue_precond_(k, 0);
+  if (use_comm_) comm_->allreduce_sum(st->red, 4, s0_);
+}
+
 void GpuCgSolver::enqueue_iteration_(int k) {
   trace::Range tr_("mcg.iteration");
+  if (opt_.recurrence == 3) {
+    enqueue_iteration_pcg_(k);
+    return;
+  }
   if (opt_.recurrence == 2) {
     enqueue_iteration_pipe_(k);
     return;
@@ -1013,7 +1124,7 @@ void GpuCgSolver::inject_fault_(int k) {
   static const double nan = std::numeric_limits<double>::quiet_NaN();
   if (L_.n_local() == 0 || rank_ != 0) return;
   double* r = opt_.recurrence == 2 ? r_.get() + L_.own_off
-              : pmat_ ? r_.get()
+              : (pmat_ || opt_.recurrence == 3) ? r_.get()  // (preconditioned: U_k's r.r carries it to the latch)
               : opt_.form.interleave == 1 ? ra_[(k + 1) & 1].get() + 2 * L_.own_off  // .x of the first owned pair
                                      : ((opt_.recurrence == 1 && (k & 1) == 0) ? r1_.get() : r_.get()) + L_.own_off;
   // the three-term carries recover r from the two p's and read a stored r only past their runs' ends:
@@ -1027,6 +1138,10 @@ void GpuCgSolver::finalize() {
   finalized_ = true;  // the single-reduction catch-up of a pending x term must run once
   if (ar_ && use_halo_) ensure_ghosts_(k_);  // the final r_m recomputes Ap_{m-1} over the ghost lines too
   else join_halo_();
+  if (opt_.recurrence == 3) {  // x_m is in place; the all-reduced r_m.r_m of the last iteration decides the flag
+    kern::cg_pcg_final(st_.get(), opt_.tol, s0_);
+    return;
+  }
   if (opt_.recurrence == 2) {  // gamma_m of the last update, all-reduced, decides the flag
     if (use_comm_) comm_->allreduce_sum(st_.get()->red, 4, s0_);
     kern::cg_pipe_final(st_.get(), opt_.tol, s0_);

@@ -35,6 +35,7 @@ struct CkptHeader {
 void GpuCgSolver::save_checkpoint(const std::string& prefix) {
   MCG_CHECK(setup_done_, "solver not set up");
   MCG_CHECK(!prefix.empty(), "checkpoint path not set");
+  MCG_CHECK(opt_.recurrence != 3, "checkpoints are not supported with a preconditioner");
   synchronize();
   const std::string path = prefix + ".rank" + std::to_string(rank_);
   const std::string tmp = path + ".tmp";
@@ -75,6 +76,7 @@ void GpuCgSolver::save_checkpoint(const std::string& prefix) {
 
 void GpuCgSolver::load_checkpoint(const std::string& prefix) {
   MCG_CHECK(setup_done_, "solver not set up");
+  MCG_CHECK(opt_.recurrence != 3, "checkpoints are not supported with a preconditioner");
   // nothing of an earlier solve may still run on either stream (a pending halo writes ghost rows)
   synchronize();
   join_halo_();
@@ -235,7 +237,9 @@ CgResult GpuCgSolver::result() {
   r.breakdown = st.breakdown != 0;
   r.beta_clamps = st.clamps;
   r.rr0_local = st.rr0;
-  r.rnorm = std::sqrt(st.done ? st.rr_final : (opt_.recurrence >= 1 ? st.red[3] : st.rr_new));
+  // (preconditioned: {r.r, r.z} of the last iteration sit in red[0], red[1])
+  r.rnorm = std::sqrt(st.done ? st.rr_final
+                              : (opt_.recurrence == 3 ? st.red[0] : (opt_.recurrence >= 1 ? st.red[3] : st.rr_new)));
   r.setup_seconds = setup_seconds_;
   float ms = 0.f;
   if (hipEventElapsedTime(&ms, ev_t0_, ev_t1_) == hipSuccess) r.solve_seconds = ms * 1e-3;
@@ -249,6 +253,16 @@ std::vector<double> GpuCgSolver::x_local() {
   if (!h.empty())
     MCG_HIP(hipMemcpy(h.data(), x_.get(), h.size() * sizeof(double), hipMemcpyDeviceToHost),
             "memcpy from device to host failed(x)");
+  return h;
+}
+
+std::vector<double> GpuCgSolver::precond_dinv() {
+  MCG_CHECK(setup_done_ && opt_.recurrence == 3, "precond_dinv: no preconditioner set");
+  synchronize();
+  std::vector<double> h(L_.n_local());
+  if (!h.empty())
+    MCG_HIP(hipMemcpy(h.data(), dinv_.get(), h.size() * sizeof(double), hipMemcpyDeviceToHost),
+            "memcpy from device to host failed(dinv)");
   return h;
 }
 

@@ -184,7 +184,7 @@ void GpuCgSolver::setup() {
   const bool scattered_user = is_user && stencil_line(spec_) == 0 && spec_.csr != nullptr &&
                               (L_.allgather ||
                                (spec_.csr->far > 0 && 4 * spec_.csr->far >= spec_.csr->rowptr[spec_.csr->n]));
-  tiles_ = opt_.recurrence >= 1 && (opt_.form.pmat != 0 || opt_.recurrence == 2) && opt_.form.tiles != 0 &&
+  tiles_ = opt_.recurrence >= 1 && opt_.recurrence != 3 && (opt_.form.pmat != 0 || opt_.recurrence == 2) && opt_.form.tiles != 0 &&
            (opt_.form.tiles == 1 || scrambled(spec_) || scattered_user);
   if (is_user) {
     user = build_local_csr(spec_, L_);
@@ -456,6 +456,7 @@ void GpuCgSolver::setup() {
   info_.halo_ahead = halo_ahead_;
   split_ = use_halo_ && opt_.overlap && !halo_ahead_;
   if (opt_.recurrence == 2) split_ = prefetch_halo_ = false;  // pipelined: the all-reduce is what overlaps
+  if (opt_.recurrence == 3) split_ = prefetch_halo_ = false;  // preconditioned: one launch, halo on the compute stream
   // all-gather overlap: the own-block slots of each aligned slice are summed while p_k's all-gather
   // is in flight (aligned_ is decided from the spec and the layout is the same kind on every rank,
   // so every rank takes the same launches)
@@ -982,12 +983,16 @@ void GpuCgSolver::setup() {
   }
   allocate_vectors_();
   g_b_ = kern::grid_for((n + 1) / 2, 256, 4);  // residual update / dot kernels: 1024 blocks (best measured)
+  if (opt_.recurrence == 3) {  // every kernel takes part in a reduction: a rank without rows still launches one block
+    g_all_ = std::max(g_all_, 1);
+    g_b_ = std::max(g_b_, 1);
+  }
   info_.grid_a = g_all_;
   info_.graphs = opt_.use_graph;
   info_.grid_odd = g_odd_;
   info_.grid_b = g_b_;
   const bool split = split_ || lean_split_;
-  fused_red_ = (opt_.recurrence == 1 && opt_.form.fused_reduce != 0) || opt_.recurrence == 2;
+  fused_red_ = (opt_.recurrence == 1 && opt_.form.fused_reduce != 0) || opt_.recurrence >= 2;
   auto groups = [](int g) { return (g + kern::kRedGroup - 1) / kern::kRedGroup; };
   // the boundary launch's partials start on a reduction-group boundary: round the interior grid up
   // (the extra blocks find no work in the grid-stride loops and contribute zero partials)
@@ -1025,6 +1030,15 @@ void GpuCgSolver::setup() {
   // pipelined: S reads w (ideal gathers) and writes q (16 B), U reads 7 and writes 6 vectors (104 B)
   if (opt_.recurrence == 2) info_.bytes_per_iter_model = (double)matrix_bytes + 120.0 * n;
   if (opt_.recurrence == 1) info_.device_bytes += (size_t)(3 * L_.ext_len - n) * 8;
+  if (opt_.recurrence == 3) {
+    setup_precond_();
+    // pass: z, p_{k-1} gathered (ideal), p_k, q written 32 B; update: x rw, p, r rw, q, dinv read, z written 64 B
+    // (Chebyshev: + d 8 B); each Chebyshev step: the matrix again, z gathered, r, d, dinv read, d, z written 48 B
+    const int m = info_.spmv_per_iteration;
+    info_.bytes_per_iter_model = (double)m * (double)matrix_bytes + (96.0 + (m > 1 ? 8.0 + 48.0 * (m - 1) : 0.0)) * n;
+    info_.device_bytes = matrix_bytes + rp64_.bytes() + b_.bytes() + dinv_.bytes();
+    for (DeviceBuffer<double>* v : vectors_()) info_.device_bytes += v->bytes();
+  }
   if (pmat_) {  // U: x rw, r rw, Ap r, p rw = 56 B; S: r, Ap 16 B + one pass over p (ideal gathers) 8 B
     info_.bytes_per_iter_model = (double)matrix_bytes + 80.0 * n;
     info_.device_bytes = matrix_bytes + (size_t)(4 * n + L_.ext_len) * 8 + rp64_.bytes();
@@ -1054,7 +1068,7 @@ void GpuCgSolver::setup() {
     if (use_halo_ && comm_->maps_peers()) xt_.allocate(L_.ext_len, "x", 8);
     halo_reg_.clear();
     for (DeviceBuffer<double>* b : {&r_, &r1_, &Ap_, &Ap1_, &p_[0], &p_[1], &ra_[0], &ra_[1], &apx_[0], &apx_[1], &w_, &xe_, &xt_,
-                                    &p_[2]})
+                                    &p_[2], &zc_[0], &zc_[1]})
       if (b->get() != nullptr) halo_reg_.push_back(b->get());
     comm_->register_halo_buffers(halo_reg_, L_.own_off, L_.row_begin);
   }
@@ -1062,6 +1076,55 @@ void GpuCgSolver::setup() {
   if (opt_.recurrence == 2) pick_pipe_order_();
   setup_done_ = true;
   setup_seconds_ = std::chrono::duration<double>(clk::now() - t0).count();
+}
+
+// Preconditioner setup: one device scan of the stored matrix (whatever the solver holds: generated or the
+// user's rows, CSR int32 / int64 or SELL-64 int32 / d16 / c8, sigma-sorted slots through their permutation)
+// for a_ii and sum_j |a_ij| per row; dinv = 1.0 / a_ii; the Gershgorin bound max_i sum_j |a_ij| / a_ii of
+// D^-1 A over all ranks through the sum all-reduce (one slot per rank), with the count of bad diagonals in
+// one more slot so every rank fails together.  The Chebyshev coefficients follow on the host.
+void GpuCgSolver::setup_precond_() {
+  const int64_t n = L_.n_local();
+  MCG_CHECK(!tiles_ && !aligned_ && !pmat_ && !ar_ && !info_.dia4 && !diav_ && win_doubles_ == 0,
+            "a preconditioner runs on plain CSR / SELL-64 storage");
+  DeviceBuffer<double> absum(std::max<int64_t>(n, 1), "A");
+  const SellDev S = sell_view();
+  if (info_.idx64)
+    kern::pcg_scan<int64_t>(pcg_fmt_(), CsrDev<int64_t>{rp64_.get(), cols_.get(), vals_.get(), n}, S, L_.own_off,
+                            dinv_.get(), absum.get(), s0_);
+  else
+    kern::pcg_scan<int32_t>(pcg_fmt_(), CsrDev<int32_t>{rp32_.get(), cols_.get(), vals_.get(), n}, S, L_.own_off,
+                            dinv_.get(), absum.get(), s0_);
+  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 1024));
+  DeviceBuffer<double> part(2 * (size_t)grid, "partials");
+  kern::pcg_dinv(dinv_.get(), absum.get(), n, part.get(), grid, s0_);
+  std::vector<double> hp(2 * (size_t)grid);
+  MCG_HIP(hipMemcpyAsync(hp.data(), part.get(), hp.size() * sizeof(double), hipMemcpyDeviceToHost, s0_),
+          "memcpy from device to host failed(A)");
+  MCG_HIP(hipStreamSynchronize(s0_), "device synchronize failed(A)");
+  double bad = 0.0, mx = 0.0;
+  for (int b = 0; b < grid; ++b) {
+    bad += hp[b];
+    mx = std::max(mx, hp[grid + b]);
+  }
+  std::vector<double> slots(world_ + 1, 0.0);
+  slots[rank_] = mx;
+  slots[world_] = bad;
+  allreduce_host_(slots.data(), world_ + 1);
+  MCG_CHECK(slots[world_] == 0.0, "preconditioning needs a positive diagonal");
+  double gersh = 0.0;
+  for (int q = 0; q < world_; ++q) gersh = std::max(gersh, slots[q]);
+  info_.precond = opt_.precond;
+  info_.gershgorin = gersh;
+  if (opt_.precond == 2) {
+    const double lmax = opt_.cheb_lmax > 0.0 ? opt_.cheb_lmax : gersh;
+    MCG_CHECK(lmax > 0.0 && std::isfinite(lmax), "Chebyshev preconditioner: no finite positive upper bound (cheb_lmax)");
+    cheb_ = cheb_coefficients(opt_.cheb_degree, lmax, opt_.cheb_ratio);
+    info_.cheb_degree = opt_.cheb_degree;
+    info_.cheb_ratio = opt_.cheb_ratio;
+    info_.cheb_lmax = lmax;
+    info_.spmv_per_iteration = opt_.cheb_degree;
+  }
 }
 
 // Pipelined CG: which branch of the fork after U_{k-1} -- S_k or the all-reduce -- is enqueued first.
@@ -1112,7 +1175,7 @@ bool GpuCgSolver::all_ranks_agree_(bool mine) {
 
 std::vector<DeviceBuffer<double>*> GpuCgSolver::vectors_() {
   return {&x_, &r_, &r1_, &Ap_, &Ap1_, &ra_[0], &ra_[1], &p_[0], &p_[1], &ape_[0], &ape_[1], &apx_[0], &apx_[1],
-          &w_, &z_, &q_, &p_[2]};
+          &w_, &z_, &q_, &p_[2], &zc_[0], &zc_[1], &dch_};
 }
 
 void GpuCgSolver::allocate_vectors_() {
@@ -1126,6 +1189,20 @@ void GpuCgSolver::allocate_vectors_() {
     z_.allocate(n, "Ap", 8);
     q_.allocate(n, "Ap", 8);
     if (opt_.pipe_rr < 0) xe_.allocate(L_.ext_len, "x", 8);  // x in the ext layout for r = b - A x
+    return;
+  }
+  if (opt_.recurrence == 3) {  // preconditioned: z and p gathered (ext, double-buffered); x, r, q, d, dinv owned
+    x_.allocate(n, "x", 8);
+    r_.allocate(n, "r", 8);
+    Ap_.allocate(n, "Ap", 8);  // q = A p
+    p_[0].allocate(L_.ext_len, "p", 8);
+    p_[1].allocate(L_.ext_len, "p", 8);
+    zc_[0].allocate(L_.ext_len, "r", 8);
+    if (opt_.precond == 2 && opt_.cheb_degree > 1) {
+      zc_[1].allocate(L_.ext_len, "r", 8);
+      dch_.allocate(n, "r", 8);
+    }
+    dinv_.allocate(n, "A", 8);
     return;
   }
   if (pmat_) {  // split pass: r, Ap, x owned only; p once in the ext layout (the only gathered vector)

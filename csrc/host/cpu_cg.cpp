@@ -83,9 +83,120 @@ void csr_spmv(const HostCsr& A, const double* x_ext, double* y) {
   });
 }
 
+void check_precond_options(const CgOptions& opt) {
+  MCG_CHECK(opt.precond >= 0 && opt.precond <= 2, "precond must be 0 (none), 1 (jacobi) or 2 (chebyshev)");
+  if (opt.precond == 0) return;
+  MCG_CHECK(opt.recurrence <= 0 || opt.recurrence == 3,
+            "invalid arguments: a preconditioner selects its own recurrence (leave recurrence on auto)");
+  MCG_CHECK(opt.checkpoint_every == 0 && opt.checkpoint_path.empty(),
+            "checkpoints are not supported with a preconditioner");
+  if (opt.precond == 2) {
+    MCG_CHECK(opt.cheb_degree >= 1 && opt.cheb_degree <= kChebMaxDegree, "cheb_degree must be in 1..16");
+    MCG_CHECK(opt.cheb_ratio > 1.0 && std::isfinite(opt.cheb_ratio), "cheb_ratio must be > 1");
+    MCG_CHECK(opt.cheb_lmax >= 0.0 && std::isfinite(opt.cheb_lmax), "cheb_lmax must be >= 0 (0 = the Gershgorin bound)");
+  }
+}
+
+ChebCoef cheb_coefficients(int degree, double lmax, double ratio) {
+  ChebCoef c;
+  c.m = degree;
+  const double lmin = lmax / ratio;
+  const double theta = (lmax + lmin) / 2, delta = (lmax - lmin) / 2, sigma = theta / delta;
+  c.inv_theta = 1.0 / theta;
+  double rho = 1.0 / sigma;
+  for (int j = 1; j < degree; ++j) {
+    const double rho_j = 1.0 / (2.0 * sigma - rho);
+    c.c1[j] = rho_j * rho;
+    c.c2[j] = 2.0 * rho_j / delta;
+    rho = rho_j;
+  }
+  return c;
+}
+
+CgResult cpu_pcg(const ProblemSpec& s, const CgOptions& opt, std::vector<double>* x_out,
+                 std::vector<double>* hist) {
+  using clk = std::chrono::steady_clock;
+  check_precond_options(opt);
+  MCG_CHECK(opt.precond != 0, "cpu_pcg needs a preconditioner");
+  CgResult res;
+  const auto t0 = clk::now();
+  RowPartition part = partition_rows(s, 1);
+  LocalLayout L = make_layout(s, part, 0);
+  HostCsr A = build_local_csr(s, L);
+  const int64_t n = L.n_local();
+  std::vector<double> b = build_rhs(s, 0, n);
+  // setup: a_ii and sum_j |a_ij| per row -> dinv, the Gershgorin bound of D^-1 A
+  std::vector<double> dinv(n);
+  double gersh = 0.0;
+  bool bad_diag = false;
+  for (int64_t i = 0; i < n; ++i) {
+    double d = 0.0, a = 0.0;
+    for (int64_t k = A.rowptr[i]; k < A.rowptr[i + 1]; ++k) {
+      if (A.cols[k] == (int32_t)(L.own_off + i)) d += A.vals[k];
+      a += std::fabs(A.vals[k]);
+    }
+    if (!(d > 0.0) || !std::isfinite(d)) bad_diag = true;
+    dinv[i] = 1.0 / d;
+    gersh = std::max(gersh, a / d);
+  }
+  MCG_CHECK(!bad_diag, "preconditioning needs a positive diagonal");
+  const bool cheb = opt.precond == 2;
+  const double lmax = opt.cheb_lmax > 0.0 ? opt.cheb_lmax : gersh;
+  const ChebCoef cc = cheb ? cheb_coefficients(opt.cheb_degree, lmax, opt.cheb_ratio) : ChebCoef();
+  std::vector<double> x(n, 0.0), r(b), p(L.ext_len, 0.0), z(L.ext_len, 0.0), q(n), d(cheb ? n : 0);
+  double* pown = p.data() + L.own_off;
+  double* zown = z.data() + L.own_off;
+  auto apply = [&] {  // z = M r
+    if (!cheb) {
+      for (int64_t i = 0; i < n; ++i) zown[i] = dinv[i] * r[i];
+      return;
+    }
+    for (int64_t i = 0; i < n; ++i) zown[i] = d[i] = (dinv[i] * r[i]) * cc.inv_theta;
+    for (int j = 1; j < cc.m; ++j) {
+      csr_spmv(A, z.data(), q.data());
+      for (int64_t i = 0; i < n; ++i) {
+        d[i] = cc.c1[j] * d[i] + cc.c2[j] * (dinv[i] * (r[i] - q[i]));
+        zown[i] += d[i];
+      }
+    }
+  };
+  const auto t1 = clk::now();
+  res.setup_seconds = std::chrono::duration<double>(t1 - t0).count();
+
+  double rn = std::sqrt(dot(r.data(), r.data(), n));
+  const double tol = opt.rtol > 0 ? opt.rtol * rn : opt.tol;  // r0 = b
+  apply();
+  std::copy(zown, zown + n, pown);
+  double rho = dot(r.data(), zown, n);
+  int it = 0;
+  for (; it < opt.maxit;) {
+    csr_spmv(A, p.data(), q.data());
+    const double alpha = rho / dot(pown, q.data(), n);
+    for (int64_t i = 0; i < n; ++i) x[i] += alpha * pown[i];
+    for (int64_t i = 0; i < n; ++i) r[i] += -alpha * q[i];
+    ++it;
+    rn = std::sqrt(dot(r.data(), r.data(), n));
+    if (hist) hist->push_back(rn);
+    if (!std::isfinite(rn)) { res.breakdown = true; break; }
+    if (rn < tol) { res.converged = true; break; }  // the reference's absolute test (CUDACG.cu:333)
+    apply();
+    const double rho_new = dot(r.data(), zown, n);
+    const double beta = rho_new / rho;
+    rho = rho_new;
+    for (int64_t i = 0; i < n; ++i) pown[i] = zown[i] + beta * pown[i];
+  }
+  res.iterations = it;
+  res.rnorm = rn;
+  res.solve_seconds = std::chrono::duration<double>(clk::now() - t1).count();
+  if (x_out) *x_out = std::move(x);
+  return res;
+}
+
 CgResult cpu_cg(const ProblemSpec& s, const CgOptions& opt, std::vector<double>* x_out,
                 std::vector<double>* hist) {
   using clk = std::chrono::steady_clock;
+  if (opt.precond != 0) return cpu_pcg(s, opt, x_out, hist);
+  check_precond_options(opt);
   CgResult res;
   const auto t0 = clk::now();
   RowPartition part = partition_rows(s, 1);
@@ -132,6 +243,7 @@ CgResult cpu_cg(const ProblemSpec& s, const CgOptions& opt, std::vector<double>*
 CgResult cpu_cg_partitioned(const ProblemSpec& s, int world, const CgOptions& opt,
                             std::vector<double>* x_out, std::vector<double>* hist) {
   using clk = std::chrono::steady_clock;
+  MCG_CHECK(opt.precond == 0, "invalid arguments: the CPU path runs a preconditioner on one rank only (sim-ranks 1)");
   CgResult res;
   const auto t0 = clk::now();
   RowPartition part = partition_rows(s, world, opt.halo_mode);

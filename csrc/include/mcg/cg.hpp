@@ -141,6 +141,14 @@ struct CgOptions {
                              // tile (direct or 16 lanes per row); -1 = auto (1 when every row has <= 16 entries, else 4)
   int recurrence = 0;        // 0 = two-pass / two-reduction (reference order), 1 = single-reduction fused pass,
                              // 2 = pipelined CG (Ghysels-Vanroose: the all-reduce overlaps the SpMV; cg_pipe.hip)
+                             // 3 = preconditioned CG (cg_pcg.hip): never set by hand, chosen when precond != 0
+  int precond = 0;           // 0 = none, 1 = Jacobi (z = D^-1 r), 2 = Chebyshev polynomial of D^-1 A (degree cheb_degree).
+                             // Beyond the reference (no preconditioner there); != 0 selects recurrence 3 and plain
+                             // CSR / SELL-64 (int32, d16, c8) storage; an explicit recurrence 1 / 2 with it is an error
+  int cheb_degree = 4;       // Chebyshev: SpMVs-equivalents per application (1..16; 1 = Jacobi scaled by 1 / theta)
+  double cheb_ratio = 30.0;  // Chebyshev: lmin = lmax / ratio (> 1), the interval the polynomial is built for
+  double cheb_lmax = 0.0;    // Chebyshev: upper bound on the spectrum of D^-1 A; 0 = the Gershgorin bound
+                             // max_i sum_j |a_ij| / a_ii (safe: the polynomial stays positive on (0, lmax])
   int pipe_rr = 0;           // pipelined CG: every |k| iterations recompute w = A r, s = A p, z = A s (their
                              // recurrences drift); k < 0 also replaces r = b - A x (true residual); 0 = off
   int halo_mode = -1;        // ghosts: 0 = column-window ranges (p2p send/recv), 1 = all-gather of equal row blocks
@@ -171,7 +179,7 @@ struct CgOptions {
 };
 
 struct CgResult {
-  int iterations = 0;        // number of SpMVs performed (= reference loop trips)
+  int iterations = 0;        // number of SpMVs performed (= reference loop trips; preconditioned: outer iterations)
   bool converged = false;
   bool breakdown = false;    // NaN/Inf in a reduction
   double rnorm = 0.0;        // final ||r||_2 (recurrence residual)
@@ -201,6 +209,31 @@ void csr_spmv(const HostCsr& A, const double* x_ext, double* y);
 // (copy, nrm2, SpMV, dot, axpy, axpy, nrm2, scal, axpy — CUDACG.cu:248-351).
 CgResult cpu_cg(const ProblemSpec& s, const CgOptions& opt, std::vector<double>* x_out,
                 std::vector<double>* rnorm_history = nullptr);
+
+// Preconditioned CG (CgOptions::precond), the oracle of the GPU's recurrence 3 (cg_pcg.hip), op for op:
+//   x0 = 0, r0 = b, z0 = M r0, p0 = z0, rho0 = r0.z0
+//   q = A p_k; alpha = rho_k / (p_k.q); x += alpha p_k; r -= alpha q; iterations = k + 1
+//   stop if ||r||_2 < tol;  z = M r; rho_{k+1} = r.z; beta = rho_{k+1} / rho_k; p_{k+1} = z + beta p_k
+// Jacobi: z = dinv o r with dinv = 1.0 / a_ii stored.  Chebyshev degree m on D^-1 A over [lmax / ratio, lmax]
+// (ChebCoef below).  cpu_cg dispatches here when opt.precond != 0.
+CgResult cpu_pcg(const ProblemSpec& s, const CgOptions& opt, std::vector<double>* x_out,
+                 std::vector<double>* rnorm_history = nullptr);
+
+// The Chebyshev recurrence's coefficients, from (m, lmax, ratio) alone (host, once; kernels take them by value):
+//   theta = (lmax + lmin) / 2, delta = (lmax - lmin) / 2, sigma = theta / delta, rho_0 = 1 / sigma
+//   d = (1 / theta) dinv o r; z = d
+//   j = 1 .. m-1: rho_j = 1 / (2 sigma - rho_{j-1}); d = c1[j] d + c2[j] dinv o (r - A z); z += d
+//   with c1[j] = rho_j rho_{j-1}, c2[j] = 2 rho_j / delta
+constexpr int kChebMaxDegree = 16;
+struct ChebCoef {
+  int m = 0;
+  double inv_theta = 0.0;
+  double c1[kChebMaxDegree] = {}, c2[kChebMaxDegree] = {};  // [1 .. m-1]
+};
+ChebCoef cheb_coefficients(int degree, double lmax, double ratio);
+// option checks shared by the CPU and GPU paths (throws mcg::Error: precond in 0..2, degree in 1..16, ratio > 1,
+// lmax >= 0, no explicit single-reduction / pipelined recurrence, no checkpoints)
+void check_precond_options(const CgOptions& opt);
 
 // Same recurrence with P virtual ranks in one process: each rank owns a
 // LocalLayout, builds its local CSR, exchanges halos per the plan (memcpy from

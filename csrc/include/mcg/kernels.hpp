@@ -493,6 +493,45 @@ void cg_pipe_dots(const double* r, const double* w, int64_t n, double* partials,
 void cg_pipe_final(CgState* st, double tol, hipStream_t stream);  // latch after the last update
 void sub_vec(const double* b, const double* y, double* out, int64_t n, hipStream_t stream);  // out = b - y
 
+// ---- preconditioned CG (csrc/gpu/cg_pcg.hip), recurrence = 3 ----
+// Outer iteration k: the PCG pass (p_k = z + beta p_{k-1} on the fly, q = A p_k, p.q), the update (x, r,
+// t = dinv o r; Jacobi: z = t and {r.r, r.z}), and for Chebyshev degree m the m - 1 steps (z += d with
+// d = c1 d + c2 dinv o (r - A z); the last one takes {r.r, r.z}).  Every kernel reduces its sums itself
+// (RedCtl) and one all-reduce of CgState::red follows the pass and the last kernel of the iteration.
+// CgState: red[0] = p.q after the pass; {red[0], red[1]} = {r.r, r.z} after the iteration; rho = r_k.z_k.
+struct PcgVectors {
+  double *x, *r, *q;         // owned rows
+  double* d;                 // owned rows: the Chebyshev increment (nullptr: Jacobi)
+  const double* dinv;        // owned rows: 1 / a_ii
+  double* z[2];              // ext layout; z[0] is written by the update, Chebyshev step j reads z[(j-1)&1], writes z[j&1]
+  const double* p_old;       // ext layout, p_{k-1}
+  double* p_new;             // ext layout, p_k
+};
+// setup scan over the stored entries: diag[i] = a_ii, absum[i] = sum_j |a_ij| of local row i (SELL-C-sigma:
+// the slot's row, through S.perm).  fmt: 0 CSR, 1 SELL-64 int32 columns, 3 SELL-64/d16, 4 SELL-64/c8
+template <typename IdxT>
+void pcg_scan(int fmt, const CsrDev<IdxT>& A, const SellDev& S, int64_t own_off, double* diag, double* absum,
+              hipStream_t stream);
+// in place diag[i] -> 1.0 / diag[i]; per block b of `grid`: part[b] = rows with diag <= 0 or non-finite,
+// part[grid + b] = max absum / diag over its rows with a good diagonal (the host finishes both)
+void pcg_dinv(double* diag_to_dinv, const double* absum, int64_t n, double* part, int grid, hipStream_t stream);
+// fmt as pcg_scan, CSR: 0 the row-length-adaptive engine, 6 thread per row (every row <= 16 entries: the choice
+// the two-reduction pass makes, SolverInfo::spmv_variant); zsel: the buffer of v.z holding z_k
+template <typename IdxT>
+void cg_pcg_pass(int fmt, int param, const CsrDev<IdxT>& A, const SellDev& S, const PcgVectors& v, int zsel,
+                 int64_t own_off, const TileRanges& tr, double* partials, int pstride, int grid, CgState* st, double tol,
+                 hipStream_t stream, const RedCtl& rc);
+// mode 0: Jacobi (z = t, sums); 1: Chebyshev degree 1 (z = t / theta, sums); 2: Chebyshev (d = z = t / theta, no
+// sums: the last step takes them; rc unused).  init: alpha = 0 (r = b, x = 0 on entry: z_0 and the first sums)
+void cg_pcg_update(int mode, const PcgVectors& v, int64_t own_off, int64_t n, double inv_theta, int init,
+                   double* partials, int pstride, int grid, CgState* st, hipStream_t stream, const RedCtl& rc);
+// Chebyshev step j: reads v.z[zin], writes v.z[zin ^ 1]; last: also the sums and the bookkeeping
+template <typename IdxT>
+void cg_pcg_cheb_step(int fmt, int param, const CsrDev<IdxT>& A, const SellDev& S, const PcgVectors& v, int zin,
+                      double c1, double c2, int last, int init, int64_t own_off, const TileRanges& tr, double* partials,
+                      int pstride, int grid, CgState* st, hipStream_t stream, const RedCtl& rc);
+void cg_pcg_final(CgState* st, double tol, hipStream_t stream);  // latch after the last iteration
+
 // out[i] = {a[i], 0} (seeds the interleaved {r, Ap} layout)
 void pack_pairs(const double* a, double2* out, int64_t n, hipStream_t stream);
 // modes: 0 = after a fused pass (conv check on the previous rr, sum 4 partials),

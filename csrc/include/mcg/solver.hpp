@@ -50,6 +50,12 @@ struct SolverInfo {
   int64_t max_row_len = 0;
   int spmv_variant = 0, spmv_param = 0;
   int recurrence = 0;
+  int precond = 0;            // CgOptions::precond in effect (recurrence 3 when != 0)
+  int cheb_degree = 0;        // Chebyshev: the degree m (0: not Chebyshev)
+  double cheb_ratio = 0.0;    // ... lmax / lmin
+  double cheb_lmax = 0.0;     // ... the upper bound used (CgOptions::cheb_lmax, or the Gershgorin bound over all ranks)
+  double gershgorin = 0.0;    // max_i sum_j |a_ij| / a_ii over all ranks (0: no preconditioner)
+  int spmv_per_iteration = 1; // SpMVs per (outer) iteration: Chebyshev degree m -> m
   int pipe_rr = 0;  // pipelined CG: residual-replacement period (0 = none)
   bool pipe_ar_first = false;  // pipelined CG: the all-reduce branch is enqueued before S (it took longer)
   double pipe_spmv_us = 0.0, pipe_allreduce_us = 0.0;  // the two branch times measured at setup
@@ -129,6 +135,9 @@ class GpuCgSolver {
   // Advances the solver like run_iterations().
   std::vector<std::pair<std::string, double>> phase_profile(int iters);
 
+  // preconditioner set: the reciprocal diagonal 1.0 / a_ii of this rank's rows, in local row order (syncs)
+  std::vector<double> precond_dinv();
+
   const SolverInfo& info() const { return info_; }
   const LocalLayout& layout() const { return L_; }
   hipStream_t stream() const { return s0_.get(); }
@@ -146,6 +155,14 @@ class GpuCgSolver {
   int enqueue_pass_(int k, bool fused_red);  // the pass over every owned row (lean_split: two launches)
   void enqueue_iteration_split_(int k);                   // materialized-p split pass (pmat_)
   void enqueue_iteration_pipe_(int k);                    // pipelined CG (recurrence 2)
+  void enqueue_iteration_pcg_(int k);                     // preconditioned CG (recurrence 3)
+  void enqueue_precond_(int k, int init);                 // U_k (+ the Chebyshev steps): x, r, z = M r and their sums
+  void setup_precond_();                                  // the diagonal scan: dinv_, the Gershgorin bound, ChebCoef
+  kern::PcgVectors pcg_vectors_(int k);
+  int pcg_fmt_() const {  // kern::cg_pcg_pass's storage codes
+    if (opt_.format == 1) return c8_ ? 4 : (d16_ ? 3 : 1);
+    return (info_.spmv_variant == 1 || info_.spmv_variant == 3) ? 6 : 0;
+  }
   void pick_pipe_order_();                                // pipelined CG: which fork branch goes first
   void spmv_plain_(const double* x_ext, double* y, hipStream_t s);  // y = A x, the format's plain SpMV
   void enqueue_split_spmv_(int k, int which, bool fused_red, int part = 0);  // part: cg_split_spmv
@@ -297,6 +314,10 @@ class GpuCgSolver {
   DeviceBuffer<double> r1_, Ap1_;  // second parity buffers of the single-reduction recurrence
   bool pipe_ar_first_ = false;
   DeviceBuffer<double> w_, z_, q_, xe_;  // pipelined CG: w = A r (ext), z = A s, q = A w, x in the ext layout
+  // preconditioned CG (recurrence 3): z in the ext layout, double-buffered by Chebyshev step; the Chebyshev
+  // increment d and the reciprocal diagonal (owned rows); r_ and Ap_ (= q) hold owned rows only
+  DeviceBuffer<double> zc_[2], dch_, dinv_;
+  ChebCoef cheb_;
   DeviceBuffer<double> xt_;  // x in the ext layout for true_residual_norm, registered with a peer-mapping
                              // communicator (its halo can only move registered buffers)
   DeviceBuffer<double> ra_[2];     // interleaved {r, Ap} pairs by parity (2 * ext_len doubles each)

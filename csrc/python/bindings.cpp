@@ -221,6 +221,21 @@ PYBIND11_MODULE(_C, m) {
       MCG_FORM_PROP(halo_pull)
       MCG_FORM_PROP(p3buf)
       .def_readwrite("pipe_rr", &CgOptions::pipe_rr)
+      .def_property("precond", [](const CgOptions& o) { return o.precond; },
+                    [](CgOptions& o, py::object v) {  // 0 | 1 | 2 or "none" | "jacobi" | "chebyshev"
+                      if (py::isinstance<py::str>(v)) {
+                        const std::string n = v.cast<std::string>();
+                        if (n == "none") o.precond = 0;
+                        else if (n == "jacobi") o.precond = 1;
+                        else if (n == "chebyshev") o.precond = 2;
+                        else fail("precond must be none, jacobi or chebyshev", n);
+                      } else {
+                        o.precond = v.cast<int>();
+                      }
+                    })
+      .def_readwrite("cheb_degree", &CgOptions::cheb_degree)
+      .def_readwrite("cheb_ratio", &CgOptions::cheb_ratio)
+      .def_readwrite("cheb_lmax", &CgOptions::cheb_lmax)
       .def_readwrite("graph_iters", &CgOptions::graph_iters)
       .def_readwrite("placement_tries", &CgOptions::placement_tries)
       .def_readwrite("placement_leads", &CgOptions::placement_leads)
@@ -291,6 +306,18 @@ PYBIND11_MODULE(_C, m) {
     d["rnorm_history"] = to_numpy(std::move(hist));
     return d;
   });
+  m.def("cpu_pcg", [](const ProblemSpec& s, const CgOptions& o) {
+    std::vector<double> x, hist;
+    CgResult r;
+    {
+      py::gil_scoped_release rel;
+      r = cpu_pcg(s, o, &x, &hist);
+    }
+    py::dict d = result_dict(r);
+    d["x"] = to_numpy(std::move(x));
+    d["rnorm_history"] = to_numpy(std::move(hist));
+    return d;
+  }, "preconditioned CG on the CPU (CgOptions.precond != 0): the oracle of the GPU's recurrence 3");
   m.def("cpu_cg_partitioned", [](const ProblemSpec& s, int world, const CgOptions& o) {
     std::vector<double> x, hist;
     CgResult r;
@@ -447,6 +474,8 @@ PYBIND11_MODULE(_C, m) {
       .def("synchronize", [](GpuCgSolver& g) { py::gil_scoped_release rel; g.synchronize(); })
       .def("result", [](GpuCgSolver& g) { return result_dict(g.result()); })
       .def("x_local", [](GpuCgSolver& g) { return to_numpy(g.x_local()); })
+      .def("precond_dinv", [](GpuCgSolver& g) { return to_numpy(g.precond_dinv()); },
+           "preconditioner set: 1.0 / a_ii of this rank's rows as the setup scan read them (local row order)")
       .def("true_residual_norm", [](GpuCgSolver& g) { py::gil_scoped_release rel; return g.true_residual_norm(); })
       .def("phase_profile", [](GpuCgSolver& g, int iters) {
         std::vector<std::pair<std::string, double>> r;
@@ -474,7 +503,14 @@ PYBIND11_MODULE(_C, m) {
         d["idx64"] = i.idx64;
         d["format"] = i.format == 5 ? "tiles" : i.format == 4 ? "sell64-aligned"
                       : i.format == 3 ? "sell64-c8" : (i.format == 2 ? "sell64-d16" : (i.format == 1 ? "sell64" : "csr"));
-        d["recurrence"] = i.recurrence == 2 ? "pipelined" : i.recurrence == 1 ? "single-reduction" : "two-reduction";
+        d["recurrence"] = i.recurrence == 3 ? "preconditioned" : i.recurrence == 2 ? "pipelined"
+                          : i.recurrence == 1 ? "single-reduction" : "two-reduction";
+        d["precond"] = i.precond == 2 ? "chebyshev" : i.precond == 1 ? "jacobi" : "none";
+        d["cheb_degree"] = i.cheb_degree;
+        d["cheb_ratio"] = i.cheb_ratio;
+        d["cheb_lmax"] = i.cheb_lmax;
+        d["gershgorin"] = i.gershgorin;
+        d["spmv_per_iteration"] = i.spmv_per_iteration;
         d["pipe_rr"] = i.pipe_rr;
         d["pipe_ar_first"] = i.pipe_ar_first;
         d["pipe_spmv_us"] = i.pipe_spmv_us;

@@ -15,7 +15,7 @@ import os
 import sys
 import time
 
-from .cli_spec import FLAGS, recurrence, tri
+from .cli_spec import FLAGS, precond, recurrence, tri
 from .utils import format_x
 
 SWITCHES = {"--no-overlap", "--no-graph", "--force-comm", "--verify", "--rehearse-ranks"}
@@ -24,18 +24,20 @@ CHOICES = {"--problem": ["demo", "poisson2d", "poisson3d", "randspd", "csr", "ra
            "--format": ["csr", "sell", "sell16", "sellc8"], "--print-x": ["auto", "yes", "no"],
            "--report": ["text", "json"], "--comm": ["dual", "single"], "--halo-mode": ["auto", "window", "allgather", "-1", "0", "1"],
            "--halo-transport": ["auto", "rccl"], "--allreduce": ["auto", "rccl", "ipc"],
-           "--transport-probe": ["auto", "off", "on", "-1", "0", "1"]}
+           "--transport-probe": ["auto", "off", "on", "-1", "0", "1"],
+           "--precond": ["none", "jacobi", "chebyshev"]}
 INTS = {"--n", "--rows", "--band", "--spread", "--scramble", "--coef", "--seed", "--gpus", "--sim-ranks", "--maxit", "--check-every",
         "--fixed-iters", "--warmup", "--blocks-per-cu", "--spmv-variant", "--checkpoint-every", "--inject-nan-at",
-        "--pipe-rr", "--reserve-cus"}
-FLOATS = {"--density", "--nnz-per-row", "--tol", "--rtol", "--watchdog"}
+        "--pipe-rr", "--reserve-cus", "--cheb-degree"}
+FLOATS = {"--density", "--nnz-per-row", "--tol", "--rtol", "--watchdog", "--cheb-ratio", "--cheb-lmax"}
 DEFAULTS = {"--problem": "demo", "--seed": 1234, "--device": "gpu", "--gpus": None, "--sim-ranks": 1,
             "--maxit": 2000, "--tol": 1e-7, "--rtol": 0.0, "--check-every": 32, "--fixed-iters": 0, "--warmup": 0,
             "--watchdog": 0.0, "--recurrence": "auto", "--interleave": "auto", "--window": "auto", "--carry": "auto",
             "--pmat": "auto", "--fused-reduce": "auto", "--halo-mode": "auto", "--blocks-per-cu": 0,
             "--spmv-variant": -1, "--checkpoint": "", "--checkpoint-every": 0, "--resume": "", "--inject-nan-at": -1,
             "--print-x": "auto", "--report": "text", "--comm": "single", "--pipe-rr": 0,
-            "--reserve-cus": 0, "--halo-transport": "auto", "--allreduce": "auto", "--transport-probe": "auto"}
+            "--reserve-cus": 0, "--halo-transport": "auto", "--allreduce": "auto", "--transport-probe": "auto",
+            "--precond": "none", "--cheb-degree": 4, "--cheb-ratio": 30.0, "--cheb-lmax": 0.0}
 
 
 def _parser() -> argparse.ArgumentParser:
@@ -126,10 +128,22 @@ def _run(args) -> int:
     C = mcg.native()
     fixed = args.fixed_iters > 0
     maxit, tol = (args.fixed_iters, -1.0) if fixed else (args.maxit, args.tol)
+    pc = {}
+    if precond(args.precond) != 0:  # the native parser's usage errors (csrc/cli/main.cpp)
+        if args.recurrence != "auto":
+            raise ValueError("invalid arguments: --precond selects its own recurrence (not with --recurrence)")
+        if args.device == "cpu" and args.sim_ranks > 1:
+            raise ValueError("invalid arguments: --precond on the cpu runs one rank (not with --sim-ranks)")
+        if args.checkpoint or args.checkpoint_every > 0 or args.resume:
+            raise ValueError("invalid arguments: checkpoints are not supported with --precond")
+        pc = dict(precond=args.precond, cheb_degree=args.cheb_degree, cheb_ratio=args.cheb_ratio,
+                  cheb_lmax=args.cheb_lmax)
     if args.device == "cpu":
         o = C.CgOptions(maxit=maxit, tol=tol)
         o.rtol = args.rtol
         o.halo_mode = _halo(args.halo_mode)
+        for k, v in pc.items():
+            setattr(o, k, v)
         res = (C.cpu_cg_partitioned(spec.native(), args.sim_ranks, o) if args.sim_ranks > 1
                else C.cpu_cg(spec.native(), o))
         x = res["x"]
@@ -139,8 +153,8 @@ def _run(args) -> int:
                          use_graph=not args.no_graph, force_comm=args.force_comm, comm_mode=args.comm,
                          format=args.format or ("csr" if spec.problem == "demo" else "sellc8"),
                          blocks_per_cu=args.blocks_per_cu, spmv_variant=args.spmv_variant,
-                         recurrence=recurrence(args.recurrence) if spec.problem != "demo" or args.recurrence != "auto"
-                         else 0,
+                         **({"recurrence": recurrence(args.recurrence) if spec.problem != "demo"
+                             or args.recurrence != "auto" else 0} if not pc else pc),
                          interleave=tri(args.interleave), window=tri(args.window), carry=tri(args.carry),
                          pmat=tri(args.pmat), fused_reduce=tri(args.fused_reduce), halo_mode=_halo(args.halo_mode),
                          rtol=args.rtol, pipe_rr=args.pipe_rr, checkpoint_every=args.checkpoint_every, checkpoint_path=args.checkpoint,
@@ -192,7 +206,8 @@ def _run(args) -> int:
                 "iterations": res["iterations"], "converged": res["converged"], "breakdown": res["breakdown"],
                 "rnorm": res["rnorm"], "true_rnorm": true_rnorm, "setup_s": res.get("setup_seconds"),
                 "solve_s": res["solve_seconds"], "it_per_s": res["iters_per_second"],
-                "device_bytes_rank0": info.get("device_bytes", 0), **_transport_report(info, world, args)}) + "\n")
+                "device_bytes_rank0": info.get("device_bytes", 0), **_transport_report(info, world, args),
+                **({"precond": args.precond} if pc else {})}) + "\n")
         elif not want_x or n > 3:
             sys.stderr.write("[mcg] problem=%s n=%d ranks=%d iterations=%d converged=%d rnorm=%.3e solve=%.4fs "
                              "(%.2f it/s)\n" % (spec.problem, n, world, res["iterations"], int(res["converged"]),

@@ -43,6 +43,10 @@ FLAGS = [
     ("--format", "csr", "csr | sell | sell16 | sellc8"),
     ("--recurrence", "auto", "auto | two | single | pipelined"),
     ("--pipe-rr", "0", "pipelined CG: residual replacement every K iterations (0 = off)"),
+    ("--precond", "jacobi", "none | jacobi | chebyshev: preconditioned CG (its own recurrence; not with --recurrence)"),
+    ("--cheb-degree", "4", "chebyshev: degree m of the polynomial in D^-1 A (1..16; m SpMVs per outer iteration)"),
+    ("--cheb-ratio", "30", "chebyshev: lmax / lmin of the interval the polynomial is built for"),
+    ("--cheb-lmax", "0", "chebyshev: upper bound on the spectrum of D^-1 A (0 = the Gershgorin bound)"),
     ("--interleave", "auto", TRI + ": {r, Ap} 16-B pairs (single-reduction SELL)"),
     ("--window", "auto", TRI + ": LDS column windows (long banded rows)"),
     ("--carry", "auto", TRI + ": line-carry stencil pass"),
@@ -85,6 +89,19 @@ def tri(v: str) -> int:
     if v in ("off", "0", "no"):
         return 0
     raise ValueError(f"expected auto|on|off, got {v!r}")
+
+
+PRECOND = {"none": 0, "jacobi": 1, "chebyshev": 2}
+
+
+def precond(v) -> int:
+    """none|jacobi|chebyshev (or 0|1|2) -> 0|1|2, the native parser's mapping."""
+    k = str(v).lower()
+    if k in PRECOND:
+        return PRECOND[k]
+    if k in ("0", "1", "2"):
+        return int(k)
+    raise ValueError(f"expected none|jacobi|chebyshev, got {v!r}")
 
 
 def recurrence(v: str) -> int:

@@ -28,6 +28,12 @@ def _opts(maxit=2000, tol=1e-7, **kw):
     ctor = {"check_every", "overlap", "use_graph", "force_comm", "format", "blocks_per_cu", "spmv_variant",
             "recurrence"}
     o = native().CgOptions(maxit=maxit, tol=tol, **{k: v for k, v in kw.items() if k in ctor})
+    if kw.get("precond", "none") in ("none", 0):  # the default: the options stay exactly as without the keyword
+        kw = {k: v for k, v in kw.items() if k != "precond"}
+    elif kw.get("recurrence", -1) not in (-1, "auto", None):
+        raise ValueError("a preconditioner selects its own recurrence: leave recurrence on auto")
+    else:
+        kw = {k: v for k, v in kw.items() if k != "recurrence"}
     for k, v in kw.items():
         if k not in ctor:
             if not hasattr(o, k):
@@ -42,7 +48,12 @@ class CGSolver:
     ``format="auto"`` (default) picks what both CLIs pick: the reference's CSR and two-reduction
     order for the built-in demo, SELL-64/c8 (falling back to /dia4, /diav, /d16, tiles as the matrix
     allows) with the auto recurrence (single-reduction pass) for every other problem, so
-    ``solve("poisson2d")`` runs the Ap-recomputing line carry."""
+    ``solve("poisson2d")`` runs the Ap-recomputing line carry.
+
+    ``precond="jacobi" | "chebyshev"`` (default "none") runs preconditioned CG instead (its own recurrence on
+    plain CSR / SELL-64 storage, csrc/gpu/cg_pcg.hip); ``cheb_degree`` (4), ``cheb_ratio`` (30) and
+    ``cheb_lmax`` (0 = the Gershgorin bound of D^-1 A) shape the Chebyshev polynomial.  An explicit
+    ``recurrence`` with it is an error."""
 
     def __init__(self, spec: ProblemSpec, maxit: int = 2000, tol: float = 1e-7, check_every: int = 32,
                  overlap: bool = True, use_graph: bool = True, format: str = "auto", force_comm: bool = False,
@@ -57,7 +68,7 @@ class CGSolver:
         if format == "auto":
             demo = getattr(spec, "problem", "") == "demo"
             format = "csr" if demo else "sellc8"
-            if not demo:
+            if not demo and tuning.get("precond", "none") in ("none", 0):
                 tuning.setdefault("recurrence", -1)
         if halo_transport not in ("auto", "rccl") or allreduce not in ("auto", "rccl", "ipc"):
             raise ValueError(f"halo_transport auto|rccl, allreduce auto|rccl|ipc; got {halo_transport!r}, {allreduce!r}")
@@ -124,6 +135,10 @@ class CGSolver:
     def x_local(self) -> np.ndarray:
         return self._s.x_local()
 
+    def precond_dinv(self) -> np.ndarray:
+        """1.0 / a_ii of this rank's rows as the preconditioner's setup scan read them (local row order)."""
+        return self._s.precond_dinv()
+
     def true_residual_norm(self) -> float:
         return self._s.true_residual_norm()
 
@@ -153,7 +168,10 @@ def solve(problem: str = "demo", device: str = "gpu", sim_ranks: int = 1, maxit:
     spec = make_problem(problem, **spec_kw)
     perm = getattr(spec, "perm", None)  # reordered user matrix: hand x back in the caller's numbering
     if device == "cpu":
-        o = _opts(maxit, tol)
+        if sim_ranks > 1 and kw.get("precond", "none") not in ("none", 0):
+            raise ValueError("the CPU path runs a preconditioner on one rank only (sim_ranks=1)")
+        o = _opts(maxit, tol, **{k: kw[k] for k in ("precond", "cheb_degree", "cheb_ratio", "cheb_lmax", "recurrence")
+                                 if k in kw})
         C = native()
         r = C.cpu_cg_partitioned(spec.native(), sim_ranks, o) if sim_ranks > 1 else C.cpu_cg(spec.native(), o)
         if perm is not None:
@@ -161,6 +179,7 @@ def solve(problem: str = "demo", device: str = "gpu", sim_ranks: int = 1, maxit:
         return r
     s = CGSolver(spec, maxit=maxit, tol=tol, **kw)
     r = s.solve()
+    r["recurrence"], r["precond"] = s.info["recurrence"], s.info["precond"]
     if perm is not None and s.env.world == 1:
         r["x_local"] = spec.unpermute(r["x_local"])
     return r
